@@ -23,6 +23,14 @@ Launch: python bench.py [--gpus N --steps K --warmup W]; for N > 1 under
 torch.distributed.run (one rank per GPU, RCCL); each rank takes its own batch
 of the same graph (weak scaling) and ranks keep one codebook via an RCCL
 all-reduce of the sufficient statistics and an all-gather of the codes.
+
+A plain run sets up, warms up, times the K steps and prints the headline
+line (metric, value, unit, ms_per_step, ...).  --dump-outputs DIR writes what
+the last timed step computed as DIR/<name>.npy (dump_outputs below).  --full
+adds everything else the benchmark measures, each in passes of its own: the
+task plan's build time, the assign's kernel events inside the timed region,
+the per-phase breakdown, the roofline figures (PMC traffic, SpMM floor,
+device copy rate) and the CPU baseline.
 """
 import argparse
 import json
@@ -43,7 +51,13 @@ def parse():
     p.add_argument("--steps", type=int, default=20)
     p.add_argument("--warmup", type=int, default=5)
     p.add_argument("--config", default="arxiv_gcn")
+    # everything beyond the headline figure (plan_ms, kernel events, per-phase
+    # breakdown, roofline, CPU baseline): passes of their own, off by default
+    p.add_argument("--full", action="store_true")
+    # the last timed step's results as DIR/<name>.npy (dump_outputs)
+    p.add_argument("--dump-outputs", metavar="DIR", default=None)
     p.add_argument("--semantics", default="update", choices=["update", "feature_update"])
+    # the --full passes' own switches
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--cpu-seconds", type=float, default=12.0)
     p.add_argument("--pmc-json", default=os.path.join(ROOT, "profiles", "pmc_latest.json"))
@@ -196,7 +210,9 @@ def main():
               and kernels.codebook_source_preferred(M))
     if use_cb:   # per batch as well: the records with out-of-batch columns -> nodes
         spmm_plan = adj.plan_codebook(B, subset, N_graph)
-    plan_ms = time_plan(adj, n, nnz, cb=(B, subset, N_graph) if use_cb else None)
+    plan_ms = None
+    if args.full:
+        plan_ms = time_plan(adj, n, nnz, cb=(B, subset, N_graph) if use_cb else None)
     # codebook state = one feature_update warm pass
     bank.feature_update(Xd, 0, nb, True, codes=codes, batch_idx=bidx)
     torch.cuda.synchronize()
@@ -214,7 +230,10 @@ def main():
     overlap = args.overlap == "on" and use_cb and not args.graph
     side = torch.cuda.Stream() if (overlap or args.overlap_whole) else None
 
+    agg = [None]    # the aggregation a step returns to its caller (--dump-outputs)
+
     def step(record):
+        agg[0] = None           # (freed before this step allocates its own)
         e = [torch.cuda.Event(enable_timing=True) for _ in range(5)] if record else None
         if record:
             e[0].record()
@@ -237,7 +256,7 @@ def main():
                 vq_update(before_assign=wk.launch)
                 fin = None if args.separate_finalize else bank.take_fused_finalize()
                 fin_fused[0] = fin is not None
-                kernels.spmm_codebook_fixup(wk, finalize=fin)     # joins the walk
+                agg[0] = kernels.spmm_codebook_fixup(wk, finalize=fin)     # joins the walk
             else:
                 bank.land_codes_on(side)
                 side.wait_stream(torch.cuda.current_stream())
@@ -272,8 +291,8 @@ def main():
             # process; multi-GPU it waits for its all-reduce: finish_update)
             fin = None if args.separate_finalize or not fuse else bank.take_fused_finalize()
             fin_fused[0] = fin is not None
-            kernels.spmm_codebook(adj.rowptr, n, nnz, Xd, F, B, codes, bank.emb_out, D,
-                                  spmm_plan, finalize=fin)
+            agg[0] = kernels.spmm_codebook(adj.rowptr, n, nnz, Xd, F, B, codes, bank.emb_out, D,
+                                           spmm_plan, finalize=fin)
             if record:
                 e[3].record()
             return
@@ -282,10 +301,10 @@ def main():
             e[2].record()
         if gat is not None:     # attention aggregation (alpha, coefficients, SpMM, normalise)
             with torch.no_grad():
-                gat.fused_forward(Xd, adj, x_first, B)
+                agg[0] = gat.fused_forward(Xd, adj, x_first, B)
         else:
-            kernels.spmm(adj.rowptr, adj.col, adj.value, n, nnz, Xd, F, X2=x_first, B=B,
-                         plan=spmm_plan)
+            agg[0] = kernels.spmm(adj.rowptr, adj.col, adj.value, n, nnz, Xd, F, X2=x_first,
+                                  B=B, plan=spmm_plan)
         if record:
             e[3].record()
 
@@ -316,14 +335,14 @@ def main():
         run = graph.replay
         barrier()
         torch.cuda.synchronize()
-    # timed region: the roofline kernel's launches carry a start/stop HIP
-    # event pair taken by hipExtLaunchKernel itself (include/vqgnn.h §5a: the
-    # kernel's own duration, no events between kernels on the stream); the
+    # timed region.  --full: the roofline kernel's launches carry a start/stop
+    # HIP event pair taken by hipExtLaunchKernel itself (include/vqgnn.h §5a:
+    # the kernel's own duration, no events between kernels on the stream); the
     # per-phase breakdown is a separate pass below.  (--graph: the replays
     # carry no events; the assign is timed in an eager pass after them)
     from vq_gnn_amd._lib import lib as _vqlib
     L = _vqlib()
-    kernel_events = not args.no_kernel_events and not args.graph
+    kernel_events = args.full and not args.no_kernel_events and not args.graph
     if kernel_events:
         L.vqgnn_assign_timing(1)
     t0 = time.perf_counter()
@@ -343,17 +362,8 @@ def main():
         return [buf[i] for i in range(n) if buf[i] > 0]
 
     assign_ms_list = read_assign_ms() if kernel_events else []
-    # per-phase breakdown (untimed for value): update | gather | aggregation
-    for _ in range(args.steps):
-        step(True)
-    torch.cuda.synchronize()
-    if not assign_ms_list:      # --no-kernel-events / --graph: a separate eager pass
-        L.vqgnn_assign_timing(1)
-        for _ in range(args.steps):
-            step(False)
-        torch.cuda.synchronize()
-        assign_ms_list = read_assign_ms()
-    bank.check_bad_init()
+    if args.dump_outputs:       # before any further pass moves the state on
+        dump_outputs(args.dump_outputs, rank, agg[0], codes, bidx, bank)
 
     dt = t1 - t0
     tvec = torch.tensor([dt, float(nnz)], dtype=torch.float64, device=dev)
@@ -367,6 +377,57 @@ def main():
         total_edges = float(nnz)
     ms_step = dt / args.steps * 1e3
     value = total_edges * args.steps / dt
+
+    def finish(result):
+        if rank == 0:
+            print(json.dumps(result))
+        if comm is not None:
+            comm.close()            # direct RCCL communicators: a clean destroy on every rank
+        if dist.is_initialized():
+            dist.destroy_process_group()
+
+    out = dict(
+        metric="edges/sec (VQ-assign + aggregate) on arxiv-shaped GCN, 1/2/4/8 MI355X",
+        value=value, unit="edges/s", n_gpus=world, steps=args.steps, warmup=args.warmup,
+        ms_per_step=ms_step, higher_is_better=True, scaling="weak", vs_baseline=None,
+        dtype="f32", data="synthetic (seeded arxiv-shaped graph, random features)",
+        config=dict(workload=f"{args.config}: one layer step (VQ {args.semantics} + EMA for "
+                             f"{nb} branches, "
+                             + ("SpMM with the out-of-batch rows read from the codebook)"
+                                if use_cb else
+                                "codeword gather, " +
+                                ("GAT attention aggregation)" if gat is not None else "SpMM)")),
+                    aggregation=("codebook_source" if use_cb else "gathered_rows"),
+                    ema_finalize=("in the aggregation's fix-up launch" if fin_fused[0]
+                                  else "own launch"),
+                    schedule=("aggregation walk on a side stream beside BN statistics + "
+                              "assign, fix-up after both" if side is not None and use_cb
+                              and not args.overlap_whole else
+                              "whole aggregation on a side stream" if side is not None
+                              else "serial"),
+                    B=B, B_prime=n - B, nnz=nnz, F=F, M=M, D=D, W=W,
+                    parallelism=f"dp{world}", world=world,
+                    backend=(args.backend if comm is not None else None),
+                    rccl_ranks=(world if comm is not None and args.backend == "nccl" else 0),
+                    devices=(1 if os.environ.get("VQGNN_BENCH_ONE_DEVICE") == "1" else world)),
+        host_issue_ms_per_step=t_issue / args.steps * 1e3,
+    )
+    if not args.full:
+        bank.check_bad_init()
+        finish(out)
+        return
+
+    # per-phase breakdown (untimed for value): update | gather | aggregation
+    for _ in range(args.steps):
+        step(True)
+    torch.cuda.synchronize()
+    if not assign_ms_list:      # --no-kernel-events / --graph: a separate eager pass
+        L.vqgnn_assign_timing(1)
+        for _ in range(args.steps):
+            step(False)
+        torch.cuda.synchronize()
+        assign_ms_list = read_assign_ms()
+    bank.check_bad_init()
 
     # VQ update = BN + assign (e0 -> e1) + the deferred finalize (e3 -> e4;
     # with the finalize fused into the aggregation's fix-up launch it is
@@ -447,43 +508,44 @@ def main():
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_leg(args, X, G, batch, bidx, subset, adj, codes0, M, D, B, nnz, nb, gat)
 
-    if rank == 0:
-        out = dict(
-            metric="edges/sec (VQ-assign + aggregate) on arxiv-shaped GCN, 1/2/4/8 MI355X",
-            value=value, unit="edges/s", n_gpus=world, steps=args.steps, warmup=args.warmup,
-            ms_per_step=ms_step, higher_is_better=True, scaling="weak", vs_baseline=None,
-            dtype="f32", data="synthetic (seeded arxiv-shaped graph, random features)",
-            config=dict(workload=f"{args.config}: one layer step (VQ {args.semantics} + EMA for "
-                                 f"{nb} branches, "
-                                 + ("SpMM with the out-of-batch rows read from the codebook)"
-                                    if use_cb else
-                                    "codeword gather, " +
-                                    ("GAT attention aggregation)" if gat is not None else "SpMM)")),
-                        aggregation=("codebook_source" if use_cb else "gathered_rows"),
-                        ema_finalize=("in the aggregation's fix-up launch" if fin_fused[0]
-                                      else "own launch"),
-                        schedule=("aggregation walk on a side stream beside BN statistics + "
-                                  "assign, fix-up after both" if side is not None and use_cb
-                                  and not args.overlap_whole else
-                                  "whole aggregation on a side stream" if side is not None
-                                  else "serial"),
-                        B=B, B_prime=n - B, nnz=nnz, F=F, M=M, D=D, W=W,
-                        parallelism=f"dp{world}", world=world,
-                        backend=(args.backend if comm is not None else None),
-                        rccl_ranks=(world if comm is not None and args.backend == "nccl" else 0),
-                        devices=(1 if os.environ.get("VQGNN_BENCH_ONE_DEVICE") == "1" else world)),
-            roofline=roofline,
-            kernels=dict(vq_update_ms=vq_ms, codeword_gather_ms=gather_ms, spmm_ms=spmm_ms,
-                         spmm=rl_spmm, vq_assign=rl_vq),
-            cpu_baseline=cpu,
-            host_issue_ms_per_step=t_issue / args.steps * 1e3,
-            plan_ms=plan_ms,
-        )
-        print(json.dumps(out))
-    if comm is not None:
-        comm.close()            # direct RCCL communicators: a clean destroy on every rank
-    if dist.is_initialized():
-        dist.destroy_process_group()
+    out.update(
+        roofline=roofline,
+        kernels=dict(vq_update_ms=vq_ms, codeword_gather_ms=gather_ms, spmm_ms=spmm_ms,
+                     spmm=rl_spmm, vq_assign=rl_vq),
+        cpu_baseline=cpu,
+        plan_ms=plan_ms,
+    )
+    finish(out)
+
+
+def dump_outputs(dirname, rank, agg, codes, bidx, bank):
+    """--dump-outputs: what the last timed step handed its caller, as float32
+    <name>.npy files (rank r > 0 of a multi-GPU run: <name>.rank<r>.npy) --
+    the aggregation's rows, the batch nodes' codes (c_indices) and the
+    codebook state (embedding, embedding_output, ema_w, cluster size and the
+    BatchNorm running statistics of every branch).  An array above 16 MB is
+    cut to a fixed, seeded sample of its rows (ascending; the row numbers in
+    <name>_rows.npy), so one dump stays below 64 MB."""
+    os.makedirs(dirname, exist_ok=True)
+    sfx = "" if rank == 0 else f".rank{rank}"
+
+    def save(name, t):
+        np.save(os.path.join(dirname, f"{name}{sfx}.npy"),
+                t.detach().to(torch.float32).cpu().numpy())
+
+    def save_rows(name, t, seed):
+        cap = (16 << 20) // (4 * t.shape[1])
+        if t.shape[0] > cap:
+            rows = torch.randperm(t.shape[0], generator=torch.Generator().manual_seed(seed))
+            rows = rows[:cap].sort().values
+            np.save(os.path.join(dirname, f"{name}_rows{sfx}.npy"), rows.numpy().astype(np.float64))
+            t = t[rows.to(t.device)]
+        save(name, t)
+
+    save_rows("aggregate", agg, 11)
+    save_rows("codes", codes[bidx.long()], 12)
+    for name in ("emb", "emb_out", "ema_w", "cs", "rm_f", "rv_f", "rm_g", "rv_g"):
+        save(f"bank_{name}", getattr(bank, name))
 
 
 def lib_digest():

@@ -20,7 +20,7 @@ for rep in ${REPS:-1 2}; do
         *=*) envs=$(echo $n | tr '+' ' ') ;;
         *) export VQGNN_LIB=$PWD/vq-gnn_amd/lib/ab_$n.so ;;
       esac
-      env $envs timeout -k 10 200 python bench.py --no-cpu-baseline --steps 30 --warmup 5 --config $cfg \
+      env $envs timeout -k 10 200 python bench.py --full --no-cpu-baseline --steps 30 --warmup 5 --config $cfg \
         --semantics $sem > $O/ab_${n}_${cfg}_${sem}_$rep.json 2> $O/ab_${n}_${cfg}_${sem}_$rep.err || exit 1
       python3 -c "import json; d=json.loads(open('$O/ab_${n}_${cfg}_${sem}_$rep.json').read().strip().splitlines()[-1]); k=d['kernels']['vq_assign']; print('$rep $cfg $sem $n', 'ms/step %.4f'%d['ms_per_step'], 'assign us %.1f'%(k['ms_per_launch']*1e3), 'frac %.3f'%k['frac'])"
     done

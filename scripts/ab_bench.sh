@@ -18,7 +18,7 @@ for rep in 1 2; do
       envs=$(echo "$v" | cut -d'|' -f2 | tr ';' ' ')
       flags=$(echo "$v" | cut -d'|' -f3)
       f=$O/${name}_${cfg}_${sem}_$rep
-      env $envs timeout -k 10 200 python bench.py --no-cpu-baseline --steps 30 --warmup 5 \
+      env $envs timeout -k 10 200 python bench.py --full --no-cpu-baseline --steps 30 --warmup 5 \
         --config $cfg --semantics $sem $flags > $f.json 2> $f.err || exit 1
       python3 -c "import json; d=json.loads(open('$f.json').read().strip().splitlines()[-1]); k=d['kernels']; print('$rep $cfg $sem $name', 'ms/step %.4f'%d['ms_per_step'], 'assign us %.1f'%(k['vq_assign']['ms_per_launch']*1e3), 'agg us %.1f'%(k['spmm_ms']*1e3), d['config'].get('aggregation'), '|', d['config'].get('order'))"
     done

@@ -16,7 +16,7 @@ for rep in 1 2; do
       envs=""
       [ "$setting" != "-" ] && envs=$(echo "$setting" | tr ';' ' ')
       f=$O/ab${i}_${cfg}_${sem}_$rep
-      env $envs timeout -k 10 200 python bench.py --no-cpu-baseline --steps 30 --warmup 5 --config $cfg \
+      env $envs timeout -k 10 200 python bench.py --full --no-cpu-baseline --steps 30 --warmup 5 --config $cfg \
         --semantics $sem > $f.json 2> $f.err || exit 1
       python3 -c "import json; d=json.loads(open('$f.json').read().strip().splitlines()[-1]); k=d['kernels']['vq_assign']; print('$rep $cfg $sem [$setting]', 'ms/step %.4f'%d['ms_per_step'], 'assign us %.1f'%(k['ms_per_launch']*1e3))"
     done

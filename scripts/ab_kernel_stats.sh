@@ -12,7 +12,7 @@ for rep in 1 2; do
     if [ "$n" = "default" ]; then unset VQGNN_LIB; else export VQGNN_LIB=$PWD/vq-gnn_amd/lib/ab_$n.so; fi
     d=$O/${n}_$rep
     timeout -k 10 200 rocprofv3 --kernel-trace --stats -d $d -o run --output-format csv \
-      -- python bench.py --steps 30 --warmup 5 --no-cpu-baseline > $d.log 2>&1 || exit 1
+      -- python bench.py --full --steps 30 --warmup 5 --no-cpu-baseline > $d.log 2>&1 || exit 1
     python3 - "$d/run_kernel_stats.csv" "$n $rep" "$PAT" <<'PY'
 import csv, re, sys
 for x in csv.DictReader(open(sys.argv[1])):

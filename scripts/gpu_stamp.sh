@@ -16,9 +16,9 @@ log smoke && timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smok
 && log pmc && TAG=${TAG}_pmc TARGET=step bash scripts/gpu_pmc.sh > $O/pmc.log 2>&1 \
 && python scripts/pmc_summary.py gpurun_out/pmc_${TAG}_pmc > $O/pmc_summary.txt \
 && python scripts/pmc_to_json.py gpurun_out/pmc_${TAG}_pmc/summary.json $O/pmc_latest.json arxiv_gcn update > /dev/null \
-&& log bench && timeout -k 10 400 python bench.py --steps 30 --warmup 5 --pmc-json $O/pmc_latest.json > $O/bench.log 2>&1 \
+&& log bench && timeout -k 10 400 python bench.py --full --steps 30 --warmup 5 --pmc-json $O/pmc_latest.json > $O/bench.log 2>&1 \
 && log rocprof && timeout -k 10 400 rocprofv3 --kernel-trace --stats -T -d $O/prof -o run --output-format csv \
-     -- python bench.py --steps 30 --warmup 5 --no-cpu-baseline --pmc-json $O/pmc_latest.json > $O/prof_bench.log 2>&1
+     -- python bench.py --full --steps 30 --warmup 5 --no-cpu-baseline --pmc-json $O/pmc_latest.json > $O/prof_bench.log 2>&1
 rc=$?
 log "chain rc=$rc"
 tail -2 $O/smoke.log

@@ -30,14 +30,14 @@ else
   python scripts/pmc_to_json.py gpurun_out/pmc_${TAG}_pmc/summary.json $O/pmc_latest.json arxiv_gcn update > /dev/null
 fi
 log bench
-timeout -k 10 400 python -u bench.py --steps 30 --warmup 5 --pmc-json $O/pmc_latest.json > $O/bench.log 2>&1 || stop $?
+timeout -k 10 400 python -u bench.py --full --steps 30 --warmup 5 --pmc-json $O/pmc_latest.json > $O/bench.log 2>&1 || stop $?
 grep -h '^{' $O/bench.log | cut -c1-400
 log rocprof
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -T -d $O/prof -o run --output-format csv \
-  -- python bench.py --steps 30 --warmup 5 --no-cpu-baseline --pmc-json $O/pmc_latest.json > $O/prof_bench.log 2>&1 || stop $?
+  -- python bench.py --full --steps 30 --warmup 5 --no-cpu-baseline --pmc-json $O/pmc_latest.json > $O/prof_bench.log 2>&1 || stop $?
 log variants
 for v in "--config arxiv_gcn --semantics feature_update" "--config arxiv_gat" "--config ppi_sage" "--config reddit_gcn"; do
-  timeout -k 10 400 python -u bench.py --steps 20 --warmup 5 $v >> $O/bench_variants.jsonl.log 2>&1 || stop $?
+  timeout -k 10 400 python -u bench.py --full --steps 20 --warmup 5 $v >> $O/bench_variants.jsonl.log 2>&1 || stop $?
 done
 grep -h '^{' $O/bench_variants.jsonl.log | cut -c1-300
 stop 0
