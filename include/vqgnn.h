@@ -681,6 +681,52 @@ int vqgnn_mapper(const int32_t* bn_row, const int32_t* bn_col, const float* bn_v
                  int32_t conv_type, int64_t* out_rowptr, int32_t* out_col, float* out_val,
                  int64_t* out_nnz, int64_t* status, void* workspace, vqgnn_stream_t stream);
 
+/* ------------------------------------------------------------------------ *
+ * 12. k-means++ codebook initialisation for nb branches at once.
+ *     Replaces the per-branch CPU MiniBatchKMeans fits of
+ *     vq_gnn_v1/models.py:147-159 that produce the (centroids, counts) of
+ *     VectorQuantizerEMA.feature_kmeans_init (vq_gnn_v2/vq.py:102-105).
+ *     Points of branch b: the normalised rows z = fma(x - shift, alpha, beta)
+ *     of columns X[:, b*D : b*D + W] (coef as vqgnn_vq_assign takes it; the
+ *     host uses W = D; W <= 8).  Distances in the assign's reference
+ *     arithmetic: |z|^2, |c|^2 sequential fp32 sums of squares, z.c a k-ordered
+ *     fma chain from fl(z0 c0), d = fma(-2, z.c, |z|^2 + |c|^2).
+ *   vqgnn_kmeans_seed: D^2 sampling, one trial per step, deterministic per
+ *     seed (tests/kmeans_ref.py restates it bit for bit):
+ *       r(b, s) = splitmix64(splitmix64(seed ^ splitmix64(b)) + s) (§9b's mix)
+ *       step 0: row r(b, 0) mod B.  After row i* is picked at step s:
+ *         centroids[b][s] = z[i*], seed_rows[b][s] = i*,
+ *         mind[i] = min(mind[i], max(d(z_i, c_s), 0)) (from +inf), mind[i*] = 0
+ *       row weight q_i = llrint(min(mind_i, 2^20) * 2^20) (exact, <= 2^40)
+ *       step s >= 1: T = sum_i q_i (exact integer); T = 0: row r(b, s) mod B,
+ *         else t = r(b, s) mod T and the first row whose inclusive prefix sum
+ *         of q exceeds t.
+ *     centroids [nb][M][ldw] (branch stride cen_bstride floats), seed_rows
+ *     int32 [nb][M].  1 + 2M launches on the stream, no host synchronisation.
+ *     Requires M <= B <= 2^23, M <= 32767, W <= min(D, 8), ldx >= nb*D with
+ *     B*ldx spanning < 4 GiB (vqgnn_vq_assign's limits).  Workspace:
+ *     vqgnn_kmeans_workspace(B, nb, M, W) bytes (0 for a bad shape).
+ *   vqgnn_kmeans_centroids: the Lloyd step's second half.  vqgnn_vq_assign
+ *     with the centroids as embedding, W = D and an EMA slab gives the labels
+ *     and, per codeword, the count n and fixed-point sums S_k (units
+ *     2^-shift_f of vqgnn_vq_stat_shifts(stat_count, 1)); this entry sets,
+ *     for update != 0 and n > 0, c_k = (float)((double)S_k * 2^-shift_f /
+ *     (double)n) (n = 0: the centroid is kept), writes counts int64 [nb][M]
+ *     (optional) and *n_empty (device int32, optional) = the number of
+ *     codewords with n = 0, and clears every slab entry it read.
+ *     update = 0: counts and n_empty of the assign alone (the last assign of
+ *     a fit: labels and counts belong to the final centroids).
+ * ------------------------------------------------------------------------ */
+size_t vqgnn_kmeans_workspace(int32_t B, int32_t nb, int32_t M, int32_t W);
+int vqgnn_kmeans_seed(const float* X, int64_t ldx, int32_t B, int32_t nb, int32_t D, int32_t M,
+                      int32_t W, const float* coef, uint64_t seed, float* centroids,
+                      int32_t ldw, int64_t cen_bstride, int32_t* seed_rows, void* workspace,
+                      vqgnn_stream_t stream);
+int vqgnn_kmeans_centroids(int64_t* ema_parts, int32_t nparts, int64_t stat_count, int32_t nb,
+                           int32_t M, int32_t W, float* centroids, int32_t ldw,
+                           int64_t cen_bstride, int32_t update, int64_t* counts,
+                           int32_t* n_empty, vqgnn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -192,6 +192,13 @@ SIGNATURES = {
     "vqgnn_coo_to_csr": (ctypes.c_int, [_c_void_p, _c_void_p, _c_void_p, _i64, _i64, _i64,
                                         _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
                                         _c_void_p]),
+    # §12 k-means++ codebook initialisation
+    "vqgnn_kmeans_workspace": (_size, [_i32, _i32, _i32, _i32]),
+    "vqgnn_kmeans_seed": (ctypes.c_int, [_c_void_p, _i64, _i32, _i32, _i32, _i32, _i32, _c_void_p,
+                                         ctypes.c_uint64, _c_void_p, _i32, _i64, _c_void_p,
+                                         _c_void_p, _c_void_p]),
+    "vqgnn_kmeans_centroids": (ctypes.c_int, [_c_void_p, _i32, _i64, _i32, _i32, _i32, _c_void_p,
+                                              _i32, _i64, _i32, _c_void_p, _c_void_p, _c_void_p]),
 }
 
 _lock = threading.Lock()

@@ -278,6 +278,58 @@ def ema_finalize_args(parts, D, W, decay, laplace, grad_scale, epsilon, cs, ema_
         rv_g=rv_g.data_ptr() if rv_g is not None else None, bad_init=bad_flag.data_ptr())
 
 
+def kmeans_seed(X, coef, D, M, seed=0, W=None):
+    """k-means++ seeds of every branch of X [B, nb*D] (include/vqgnn.h §12):
+    D^2 sampling over the normalised rows fma(x - shift, alpha, beta) of coef
+    [6, nb*D], deterministic per seed, no host synchronisation.
+    -> (centroids [nb, M, W] float32, seed_rows [nb, M] int32)."""
+    require_gpu(X, "kmeans_seed")
+    require_gpu(coef, "kmeans_seed")
+    B, F = X.shape
+    D, M = int(D), int(M)
+    W = D if W is None else int(W)
+    if D <= 0 or F % D != 0:
+        raise ValueError(f"kmeans_seed: X has {F} columns, not a multiple of D={D}")
+    nb = F // D
+    if coef.dtype != torch.float32 or tuple(coef.shape) != (6, F) or not coef.is_contiguous():
+        raise ValueError(f"kmeans_seed: coef must be a contiguous float32 [6, {F}]")
+    L = lib()
+    dev = X.device
+    ws = workspace(L.vqgnn_kmeans_workspace(B, nb, M, W), dev)
+    cent = torch.empty(nb, M, max(W, 1), dtype=torch.float32, device=dev)
+    rows = torch.empty(nb, M, dtype=torch.int32, device=dev)
+    check(L.vqgnn_kmeans_seed(ptr(X), _ld(X), B, nb, D, M, W, ptr(coef),
+                              int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(cent), cent.stride(1),
+                              cent.stride(0), ptr(rows), ptr(ws), stream_ptr()), "kmeans_seed")
+    return cent, rows
+
+
+def kmeans_centroids(stats, centroids, stat_count, update=True, counts=None, n_empty=None):
+    """The Lloyd step's centroid update from a vq_assign statistic slab
+    [P, nb, M, W+1] (include/vqgnn.h §12): centroids [nb, M, ldw] <- mean of
+    their rows (kept where a cluster is empty) when ``update``; the slab is
+    cleared.  -> (counts [nb, M] int64, n_empty [1] int32: empty clusters)."""
+    require_gpu(stats, "kmeans_centroids")
+    require_gpu(centroids, "kmeans_centroids")
+    if stats.dtype != torch.int64 or stats.dim() != 4 or not stats.is_contiguous():
+        raise ValueError("kmeans_centroids: the statistic slab is a contiguous int64 "
+                         "[P, nb, M, W+1]")
+    P, nb, M, W1 = stats.shape
+    if (centroids.dtype != torch.float32 or centroids.dim() != 3 or
+            tuple(centroids.shape[:2]) != (nb, M) or centroids.stride(2) != 1):
+        raise ValueError(f"kmeans_centroids: centroids must be float32 [{nb}, {M}, ldw]")
+    dev = stats.device
+    if counts is None:
+        counts = torch.empty(nb, M, dtype=torch.int64, device=dev)
+    if n_empty is None:
+        n_empty = torch.empty(1, dtype=torch.int32, device=dev)
+    check(lib().vqgnn_kmeans_centroids(ptr(stats), P, int(stat_count), nb, M, W1 - 1,
+                                       ptr(centroids), centroids.stride(1), centroids.stride(0),
+                                       int(bool(update)), ptr(counts), ptr(n_empty),
+                                       stream_ptr()), "kmeans_centroids")
+    return counts, n_empty
+
+
 def gather_codewords(subset, B, codes, emb_out, D, col_offset=0, want_x=True,
                      want_codes=False, nb=None):
     """models.py:168-173 for all branches: returns (xt [n-B, nb*D] or None,

@@ -107,7 +107,7 @@ class LowRankGNNLayer(torch.nn.Module):
                  cluster, ln_para, no_second_fc, kmeans_iter, EMA_flag, split, kmeans_init,
                  dropbranch, skip, use_gcn, commitment_cost, grad_normalize_scale, hook,
                  weight_ahead, warm_up_flag, momentum, conv_type, transformer_flag,
-                 vq_update_in_backward=False):
+                 vq_update_in_backward=False, device_kmeans_init=False, kmeans_seed=0):
         super().__init__()
         self.weight_ahead = weight_ahead
         if self.weight_ahead:
@@ -133,6 +133,12 @@ class LowRankGNNLayer(torch.nn.Module):
         self.num_M = num_M
         self.num_N = num_N
         self.vq_update_in_backward = vq_update_in_backward
+        # opt-in: k-means codebooks fitted on the device in the first training
+        # forward (VQBank.kmeans_fit; kmeans_init=True stays v2's no-op)
+        self.device_kmeans_init = bool(device_kmeans_init)
+        self.kmeans_iter = int(kmeans_iter)
+        self.kmeans_seed = int(kmeans_seed)
+        self.kmeans_result = None     # (centroids, counts, labels, seed_rows) of the fit
 
         if self.conv_type != 'GAT':
             self.conv = OurGCNConv(in_channels, in_channels, normalize=False)
@@ -176,6 +182,21 @@ class LowRankGNNLayer(torch.nn.Module):
         self._bank.feature_update(x, 0, self.num_branch, self.training, codes=self._codes,
                                   batch_idx=batch_idx)
 
+    def _device_kmeans_init(self, x):
+        """v1's k-means initialisation (vq_gnn_v1/models.py:147-159) for all
+        branches on the device, written as VectorQuantizerEMA.feature_kmeans_init
+        writes it (vq.py:102-105): feature halves of _embedding, _ema_cluster_size
+        and _ema_w = centroid * count."""
+        bank, D = self._bank, self.num_D
+        cent, counts, labels, seed_rows = bank.kmeans_fit(x, 0, self.num_branch,
+                                                          self.kmeans_iter, self.kmeans_seed)
+        with torch.no_grad():
+            cnt = counts.to(torch.float32)
+            bank.emb[:, :, :D] = cent
+            bank.cs.copy_(cnt)
+            bank.ema_w[:, :, :D] = cent * cnt.unsqueeze(2)
+        self.kmeans_result = (cent, counts, labels, seed_rows)
+
     def _backward_vq_update(self, x_detached, grad_B, batch_idx):
         """The v1 hook semantics (models.py:39-56) for all branches at once."""
         self._bank.update(x_detached, grad_B, 0, self.num_branch, True, codes=self._codes,
@@ -205,6 +226,8 @@ class LowRankGNNLayer(torch.nn.Module):
         need = [i for i in branch_idx if (not self.gnn_block[i].inited) or unlabeled]
         if len(need) == self.num_branch:
             xc = x_det if x_det.stride(1) == 1 else x_det.contiguous()
+            if self.device_kmeans_init and self.training and self.kmeans_result is None:
+                self._device_kmeans_init(xc)
             self._batched_init(xc, batch_idx)
         else:
             for i in need:
@@ -260,7 +283,7 @@ class LowRankGNN(torch.nn.Module):
                  skip=True, use_gcn=False, commitment_cost=0.5, grad_scale=(1, 1), act='relu',
                  weight_ahead=False, bn_flag=False, warm_up_flag=False, momentum=0.1,
                  conv_type='GCN', transformer_flag=False, alpha_dropout_flag=False,
-                 vq_update_in_backward=False):
+                 vq_update_in_backward=False, device_kmeans_init=False, kmeans_seed=0):
         super().__init__()
         self.num_layers = num_layers
         self.skip = skip
@@ -276,7 +299,8 @@ class LowRankGNN(torch.nn.Module):
                       commitment_cost=commitment_cost, grad_normalize_scale=grad_scale,
                       hook=True, weight_ahead=weight_ahead, warm_up_flag=warm_up_flag,
                       momentum=momentum, conv_type=conv_type, transformer_flag=transformer_flag,
-                      vq_update_in_backward=vq_update_in_backward)
+                      vq_update_in_backward=vq_update_in_backward,
+                      device_kmeans_init=device_kmeans_init, kmeans_seed=kmeans_seed)
         self.convs, self.batch_norms = torch.nn.ModuleList(), torch.nn.ModuleList()
         self.convs.append(LowRankGNNLayer(in_channels, hidden_channels, dropout, num_M, num_D,
                                           num_N, dropbranch=0, **common))

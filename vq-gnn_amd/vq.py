@@ -356,6 +356,53 @@ class VQBank(nn.Module):
             self._clean(D, b0, nbr)
             self._finish()
 
+    kmeans_n_empty = None     # device int32 [1]: empty clusters of the last kmeans_fit
+
+    def kmeans_fit(self, X, b0, nbr, iters, seed, codes=None, batch_idx=None):
+        """k-means codebooks for branches [b0, b0+nbr) of X [B, nbr*D] on the
+        device, replacing v1's per-branch CPU MiniBatchKMeans
+        (vq_gnn_v1/models.py:147-159): k-means++ seeding, ``iters`` Lloyd
+        steps (assign + centroid update) and a last assign, one launch
+        sequence for all branches, no host synchronisation (include/vqgnn.h
+        §12).  The points are X normalised with the coefficients a
+        training-mode feature_update would compute for this input (same
+        bn_arith, same layout rule), taken on throwaway running statistics:
+        nothing in the bank changes (v1: BatchNorm1d(track_running_stats=
+        False)).  -> (centroids [nbr, M, D], counts [nbr, M] int64, labels
+        [nbr, B] int64, seed_rows [nbr, M] int32); labels and counts belong
+        to the returned centroids, labels are also scattered through codes /
+        batch_idx when given; kmeans_n_empty holds the empty-cluster count."""
+        if self.comm is not None:
+            raise NotImplementedError("kmeans_fit: multi-GPU initialisation is not implemented")
+        self.finish_update()
+        self.sync_codes()
+        D, M, F = self.D, self.M, nbr * self.D
+        sl = self._sel(b0, nbr)
+        B = X.shape[0]
+        if B <= 1:
+            raise ValueError("Expected more than 1 value per channel when training")
+        if M > B:
+            raise ValueError(f"kmeans_fit: {M} codewords from {B} rows")
+        ax, _ = self._arith(X, None)
+        coef, _, _ = kernels.bn_stats_finalize(X, None, F, BN_TRAIN, 0.1, 1e-5, 0.0, 0.0, 0.0,
+                                               self.rm_f[sl].clone(), self.rv_f[sl].clone(),
+                                               D=D, arith_x=ax, ref_threads=self._threads())
+        cent, seed_rows = kernels.kmeans_seed(X, coef, D, M, seed)
+        labels = torch.empty(nbr, B, dtype=torch.int64, device=X.device)
+        counts = n_empty = None
+        for it in range(int(iters) + 1):
+            last = it == int(iters)
+            stats = kernels.vq_assign(X, None, coef, 1.0, cent, D, D,
+                                      idx_out=labels if last else None,
+                                      codes=codes if last else None,
+                                      batch_idx=batch_idx if last else None, want_stats=True,
+                                      stat_count=B, stats_out=self._slab(D, b0, nbr))
+            counts, n_empty = kernels.kmeans_centroids(stats, cent, B, update=not last,
+                                                       counts=counts, n_empty=n_empty)
+            self._clean(D, b0, nbr)
+        self.kmeans_n_empty = n_empty
+        return cent, counts, labels, seed_rows
+
     def finish_update(self):
         """Complete an update(defer=True): wait for the EMA-statistics
         all-reduce (multi-GPU; a stream wait, not a host wait) and run the
