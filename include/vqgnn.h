@@ -727,6 +727,53 @@ int vqgnn_kmeans_centroids(int64_t* ema_parts, int32_t nparts, int64_t stat_coun
                            int64_t cen_bstride, int32_t update, int64_t* counts,
                            int32_t* n_empty, vqgnn_stream_t stream);
 
+/* ------------------------------------------------------------------------ *
+ * 13. Dead-codeword revival for nb branches at once.  The EMA only shrinks
+ *     a codeword that stops being chosen (cs *= decay); this entry moves such
+ *     codewords onto rows of the batch, chosen by §12's D^2 step against the
+ *     current codebook.  Points z_i, distance d, weights q_i, r(b, s) and the
+ *     draw (T = 0: row r mod B, else t = r mod T and the first row whose
+ *     inclusive prefix sum of q exceeds t) are §12's, W = D.
+ *   Slots: the m with cluster_size[b][m] < threshold (fp32 compare: a NaN is
+ *     not dead) in ascending m, the first R = max_revive of them:
+ *     n_slots[b] = min(n_dead[b], R), slots int32 [nb][R], unused entries -1.
+ *   Initial mind: labels int64 [nb][B] = the assign's indices against the
+ *     current embedding (vqgnn_vq_assign's idx_out); mind_i = max(d(z_i,
+ *     embedding[b][labels_i][:D]), 0); a label outside [0, M) gives mind_i =
+ *     0 (never drawn by weight, nothing read out of range).
+ *   Steps s = 0 .. n_slots[b]-1, branches independently: the drawn row i*
+ *     becomes codeword m = slots[b][s], rows[b][s] = i* (int32 [nb][R],
+ *     unused entries -1), then mind_i = min(mind_i, max(d(z_i, z_i*), 0)) and
+ *     mind_i* = 0.  Written for each revived m and k < D, one fp32 rounding
+ *     each:
+ *       embedding[b][m][k] = z_i*[k]          cluster_size[b][m] = init_count
+ *       ema_w[b][m][k] = z_i*[k] * init_count
+ *       ema_w[b][m][D+k] = embedding[b][m][D+k] * init_count   (ldw >= 2D: the
+ *         gradient half of the codeword stays, embedding = ema_w / cs holds)
+ *       embedding_output[b][m][k] = fl(fl(z_i*[k] * sqrtf(rv_f + 1e-5f)) + rm_f)
+ *         (vqgnn_vq_ema_finalize's feature half; rm_f / rv_f [nb][D])
+ *       codes[batch_idx[i*] * ldc + b] = m    (codes != NULL)
+ *     Nothing else is written: live codewords, the gradient halves of
+ *     embedding / embedding_output, BatchNorm state and statistic slabs stay.
+ *     Nodes outside the batch whose stored code is a revived slot keep that
+ *     code until they are next assigned (as after any codebook move).
+ *   ema_w / embedding / embedding_output share ldw (= D or >= 2D) and
+ *     emb_bstride.  1 + 2R launches on the stream (staging + slots, initial
+ *     mind, R picks, R - 1 folds), no allocation, no host synchronisation.
+ *     Requires M <= B <= 2^23, M <= 32767, D <= 8, 1 <= R <= M, init_count >=
+ *     threshold, ldx >= nb*D with B*ldx spanning < 4 GiB.  Workspace:
+ *     vqgnn_vq_revive_workspace(B, nb, D, M, R) bytes (0 for a bad shape).
+ *     tests/revive_ref.py restates it bit for bit.
+ * ------------------------------------------------------------------------ */
+size_t vqgnn_vq_revive_workspace(int32_t B, int32_t nb, int32_t D, int32_t M, int32_t max_revive);
+int vqgnn_vq_revive(const float* X, int64_t ldx, int32_t B, int32_t nb, int32_t D, int32_t M,
+                    const float* coef, const int64_t* labels, float threshold, int32_t max_revive,
+                    float init_count, uint64_t seed, float* cluster_size, int64_t cs_bstride,
+                    float* ema_w, float* embedding, float* embedding_output, int32_t ldw,
+                    int64_t emb_bstride, const float* rm_f, const float* rv_f, int16_t* codes,
+                    int64_t ldc, const int64_t* batch_idx, int32_t* n_slots, int32_t* slots,
+                    int32_t* rows, void* workspace, vqgnn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -199,6 +199,13 @@ SIGNATURES = {
                                          _c_void_p, _c_void_p]),
     "vqgnn_kmeans_centroids": (ctypes.c_int, [_c_void_p, _i32, _i64, _i32, _i32, _i32, _c_void_p,
                                               _i32, _i64, _i32, _c_void_p, _c_void_p, _c_void_p]),
+    # §13 dead-codeword revival
+    "vqgnn_vq_revive_workspace": (_size, [_i32, _i32, _i32, _i32, _i32]),
+    "vqgnn_vq_revive": (ctypes.c_int, [_c_void_p, _i64, _i32, _i32, _i32, _i32, _c_void_p,
+                                       _c_void_p, _f32, _i32, _f32, ctypes.c_uint64, _c_void_p,
+                                       _i64, _c_void_p, _c_void_p, _c_void_p, _i32, _i64,
+                                       _c_void_p, _c_void_p, _c_void_p, _i64, _c_void_p,
+                                       _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
 }
 
 _lock = threading.Lock()

@@ -330,6 +330,73 @@ def kmeans_centroids(stats, centroids, stat_count, update=True, counts=None, n_e
     return counts, n_empty
 
 
+def vq_revive(X, coef, labels, D, threshold, max_revive, init_count, seed, cs, ema_w, emb,
+              emb_out, rm_f, rv_f, codes=None, batch_idx=None):
+    """Dead-codeword revival for every branch of X [B, nb*D] (include/vqgnn.h
+    §13): the first ``max_revive`` codewords with cs < threshold of each
+    branch move onto rows drawn by the k-means++ D^2 step against the current
+    codebook (labels [nb, B] int64: the assign's indices), in place on cs /
+    ema_w / emb / emb_out; the revived rows' codes go through codes /
+    batch_idx when given.  No host synchronisation.
+    -> (n_slots [nb] int32, slots [nb, R] int32, rows [nb, R] int32), -1 in
+    unused entries."""
+    for t in (X, coef, labels, cs, emb):
+        require_gpu(t, "vq_revive")
+    B, F = X.shape
+    D, R = int(D), int(max_revive)
+    if D <= 0 or F % D != 0:
+        raise ValueError(f"vq_revive: X has {F} columns, not a multiple of D={D}")
+    nb = F // D
+    if emb.dim() != 3 or emb.shape[0] != nb or emb.stride(2) != 1 or \
+            emb.stride(1) != emb.shape[2]:
+        raise ValueError(f"vq_revive: the codebook must be [{nb}, M, ldw], row-major per branch")
+    M, ldw = emb.shape[1], emb.shape[2]
+    if not (ema_w.stride() == emb.stride() == emb_out.stride()) or \
+            not (ema_w.shape == emb.shape == emb_out.shape):
+        raise ValueError("vq_revive: ema_w / embedding / output must share one layout")
+    if any(t.dtype != torch.float32 for t in (X, cs, ema_w, emb, emb_out, rm_f, rv_f)):
+        raise ValueError("vq_revive: float32 state expected")
+    if tuple(cs.shape) != (nb, M) or cs.stride(1) != 1:
+        raise ValueError(f"vq_revive: cs must be [{nb}, {M}] with unit column stride")
+    if coef.dtype != torch.float32 or tuple(coef.shape) != (6, F) or not coef.is_contiguous():
+        raise ValueError(f"vq_revive: coef must be a contiguous float32 [6, {F}]")
+    if labels.dtype != torch.int64 or tuple(labels.shape) != (nb, B) or \
+            not labels.is_contiguous():
+        raise ValueError(f"vq_revive: labels must be a contiguous int64 [{nb}, {B}]")
+    for t in (rm_f, rv_f):
+        if tuple(t.shape) != (nb, D) or not t.is_contiguous():
+            raise ValueError(f"vq_revive: running statistics must be contiguous [{nb}, {D}]")
+    if not 1 <= R <= M:
+        raise ValueError(f"vq_revive: max_revive={R} outside [1, M={M}]")
+    if M > B:
+        raise ValueError(f"vq_revive: {M} codewords from {B} rows")
+    if float(init_count) < float(threshold):
+        raise ValueError("vq_revive: init_count below the threshold revives dead codewords")
+    ldc = 0
+    if codes is not None:
+        if codes.dtype != torch.int16 or codes.stride(1) != 1 or batch_idx is None:
+            raise ValueError("vq_revive: codes must be an int16 [N, ldc] row-major view with "
+                             "batch_idx")
+        ldc = codes.stride(0)
+    L = lib()
+    dev = X.device
+    nbytes = L.vqgnn_vq_revive_workspace(B, nb, D, M, R)
+    if nbytes == 0:
+        raise ValueError(f"vq_revive: unsupported shape B={B} nb={nb} D={D} M={M} R={R}")
+    ws = workspace(nbytes, dev)
+    n_slots = torch.empty(nb, dtype=torch.int32, device=dev)
+    slots = torch.empty(nb, R, dtype=torch.int32, device=dev)
+    rows = torch.empty(nb, R, dtype=torch.int32, device=dev)
+    check(L.vqgnn_vq_revive(ptr(X), _ld(X), B, nb, D, M, ptr(coef), ptr(labels),
+                            float(threshold), R, float(init_count),
+                            int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(cs), cs.stride(0), ptr(ema_w),
+                            ptr(emb), ptr(emb_out), ldw, emb.stride(0), ptr(rm_f), ptr(rv_f),
+                            ptr(codes), ldc, ptr(batch_idx) if codes is not None else None,
+                            ptr(n_slots), ptr(slots), ptr(rows), ptr(ws), stream_ptr()),
+          "vq_revive")
+    return n_slots, slots, rows
+
+
 def gather_codewords(subset, B, codes, emb_out, D, col_offset=0, want_x=True,
                      want_codes=False, nb=None):
     """models.py:168-173 for all branches: returns (xt [n-B, nb*D] or None,

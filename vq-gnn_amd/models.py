@@ -29,6 +29,17 @@ from .sparse import as_csr
 from .vq import VectorQuantizerEMA, VQBank
 
 
+_M64 = (1 << 64) - 1
+
+
+def _mix64(z):
+    """splitmix64 finaliser (include/vqgnn.h §9b's mix, on the host)."""
+    z = (z + 0x9E3779B97F4A7C15) & _M64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    return z ^ (z >> 31)
+
+
 class LowRankGNNBlock(torch.nn.Module):
     """Reference: models.py:11-63.  Holds one branch's ``vq`` and its
     ``c_indices`` (a column view of the layer's packed codes)."""
@@ -107,7 +118,9 @@ class LowRankGNNLayer(torch.nn.Module):
                  cluster, ln_para, no_second_fc, kmeans_iter, EMA_flag, split, kmeans_init,
                  dropbranch, skip, use_gcn, commitment_cost, grad_normalize_scale, hook,
                  weight_ahead, warm_up_flag, momentum, conv_type, transformer_flag,
-                 vq_update_in_backward=False, device_kmeans_init=False, kmeans_seed=0):
+                 vq_update_in_backward=False, device_kmeans_init=False, kmeans_seed=0,
+                 revive_dead_every=0, revive_threshold=1e-2, revive_max=None,
+                 revive_init_count=1.0):
         super().__init__()
         self.weight_ahead = weight_ahead
         if self.weight_ahead:
@@ -139,6 +152,15 @@ class LowRankGNNLayer(torch.nn.Module):
         self.kmeans_iter = int(kmeans_iter)
         self.kmeans_seed = int(kmeans_seed)
         self.kmeans_result = None     # (centroids, counts, labels, seed_rows) of the fit
+        # opt-in: after every revive_dead_every-th batched VQ call of a
+        # training forward, codewords whose EMA cluster size fell below
+        # revive_threshold restart on rows of that batch (VQBank.revive)
+        self.revive_dead_every = int(revive_dead_every)
+        self.revive_threshold = float(revive_threshold)
+        self.revive_max = max(1, num_M // 8) if revive_max is None else int(revive_max)
+        self.revive_init_count = float(revive_init_count)
+        self.revive_result = None     # (n_slots, slots, rows) of the last revival
+        self._vq_calls = 0
 
         if self.conv_type != 'GAT':
             self.conv = OurGCNConv(in_channels, in_channels, normalize=False)
@@ -181,6 +203,27 @@ class LowRankGNNLayer(torch.nn.Module):
         sequence: feature_update + c_indices scatter."""
         self._bank.feature_update(x, 0, self.num_branch, self.training, codes=self._codes,
                                   batch_idx=batch_idx)
+        self._maybe_revive(x, batch_idx)
+
+    def _maybe_revive(self, x, batch_idx):
+        """Count the batched VQ calls of training forwards; after every
+        revive_dead_every-th one, revive over all branches on that call's x
+        with seed = mix(kmeans_seed ^ mix(call number)) (include/vqgnn.h §9b's
+        mix), so every revival draws its own rows."""
+        if not self.training or self.revive_dead_every <= 0:
+            return
+        self._vq_calls += 1
+        if self._vq_calls % self.revive_dead_every != 0:
+            return
+        seed = _mix64((self.kmeans_seed & _M64) ^ _mix64(self._vq_calls))
+        self.revive_result = self._bank.revive(
+            x, 0, self.num_branch, self.revive_threshold, seed, self.revive_max,
+            self.revive_init_count, codes=self._codes, batch_idx=batch_idx)
+
+    def codebook_health(self, threshold=None):
+        """VQBank.health of this layer's codebooks -> (n_dead int32 [nb],
+        perplexity float32 [nb]); threshold defaults to revive_threshold."""
+        return self._bank.health(self.revive_threshold if threshold is None else threshold)
 
     def _device_kmeans_init(self, x):
         """v1's k-means initialisation (vq_gnn_v1/models.py:147-159) for all
@@ -201,6 +244,7 @@ class LowRankGNNLayer(torch.nn.Module):
         """The v1 hook semantics (models.py:39-56) for all branches at once."""
         self._bank.update(x_detached, grad_B, 0, self.num_branch, True, codes=self._codes,
                           batch_idx=batch_idx)
+        self._maybe_revive(x_detached, batch_idx)
 
     def forward(self, x, batch_A, warm_up_rate, unlabeled):
         errors, X_B_norms, quantized_norms = [], [], []
@@ -283,7 +327,9 @@ class LowRankGNN(torch.nn.Module):
                  skip=True, use_gcn=False, commitment_cost=0.5, grad_scale=(1, 1), act='relu',
                  weight_ahead=False, bn_flag=False, warm_up_flag=False, momentum=0.1,
                  conv_type='GCN', transformer_flag=False, alpha_dropout_flag=False,
-                 vq_update_in_backward=False, device_kmeans_init=False, kmeans_seed=0):
+                 vq_update_in_backward=False, device_kmeans_init=False, kmeans_seed=0,
+                 revive_dead_every=0, revive_threshold=1e-2, revive_max=None,
+                 revive_init_count=1.0):
         super().__init__()
         self.num_layers = num_layers
         self.skip = skip
@@ -300,7 +346,9 @@ class LowRankGNN(torch.nn.Module):
                       hook=True, weight_ahead=weight_ahead, warm_up_flag=warm_up_flag,
                       momentum=momentum, conv_type=conv_type, transformer_flag=transformer_flag,
                       vq_update_in_backward=vq_update_in_backward,
-                      device_kmeans_init=device_kmeans_init, kmeans_seed=kmeans_seed)
+                      device_kmeans_init=device_kmeans_init, kmeans_seed=kmeans_seed,
+                      revive_dead_every=revive_dead_every, revive_threshold=revive_threshold,
+                      revive_max=revive_max, revive_init_count=revive_init_count)
         self.convs, self.batch_norms = torch.nn.ModuleList(), torch.nn.ModuleList()
         self.convs.append(LowRankGNNLayer(in_channels, hidden_channels, dropout, num_M, num_D,
                                           num_N, dropbranch=0, **common))

@@ -403,6 +403,61 @@ class VQBank(nn.Module):
         self.kmeans_n_empty = n_empty
         return cent, counts, labels, seed_rows
 
+    def revive(self, X, b0, nbr, threshold, seed, max_revive, init_count=1.0, codes=None,
+               batch_idx=None):
+        """Dead-codeword restart for branches [b0, b0+nbr) of X [B, nbr*D] on
+        the device (include/vqgnn.h §13): in each branch the first
+        ``max_revive`` codewords with cs < threshold (ascending index) move
+        onto rows of X drawn by the k-means++ D^2 step against the current
+        codebook, with cs = init_count and ema_w = codeword * init_count; the
+        gradient halves stay.  The points are X normalised as kmeans_fit
+        normalises it (training-mode coefficients on throwaway running
+        statistics); BatchNorm state, live codewords and the statistic slabs
+        are untouched.  The revived rows' codes are scattered through codes /
+        batch_idx when given; other nodes whose stored code is a revived slot
+        keep it until they are next assigned.  No host synchronisation.
+        -> (n_slots [nbr], slots [nbr, max_revive], rows [nbr, max_revive])
+        int32 device tensors, -1 in unused entries."""
+        if self.comm is not None:
+            raise NotImplementedError("revive: multi-GPU revival is not implemented")
+        D, M, F = self.D, self.M, nbr * self.D
+        B = X.shape[0]
+        if float(init_count) < float(threshold):
+            raise ValueError(f"revive: init_count {init_count} below the threshold {threshold} "
+                             "would leave the revived codewords dead")
+        if not 1 <= int(max_revive) <= M:
+            raise ValueError(f"revive: max_revive={max_revive} outside [1, M={M}]")
+        if M > B:
+            raise ValueError(f"revive: {M} codewords from {B} rows")
+        if B <= 1:
+            raise ValueError("Expected more than 1 value per channel when training")
+        self.finish_update()
+        self.sync_codes()
+        sl = self._sel(b0, nbr)
+        ax, _ = self._arith(X, None)
+        coef, _, _ = kernels.bn_stats_finalize(X, None, F, BN_TRAIN, 0.1, 1e-5, 0.0, 0.0, 0.0,
+                                               self.rm_f[sl].clone(), self.rv_f[sl].clone(),
+                                               D=D, arith_x=ax, ref_threads=self._threads())
+        labels = torch.empty(nbr, B, dtype=torch.int64, device=X.device)
+        kernels.vq_assign(X, None, coef, 1.0, self.emb[sl], D, D, idx_out=labels,
+                          want_stats=False)
+        return kernels.vq_revive(X, coef, labels, D, threshold, max_revive, init_count, seed,
+                                 self.cs[sl], self.ema_w[sl], self.emb[sl], self.emb_out[sl],
+                                 self.rm_f[sl], self.rv_f[sl], codes=codes, batch_idx=batch_idx)
+
+    def health(self, threshold):
+        """Codebook usage from the EMA cluster sizes, on the bank's device with
+        no host synchronisation -> (n_dead int32 [nb]: codewords with cs <
+        threshold, perplexity float32 [nb] = exp(-sum p log p), p = cs /
+        sum(cs), 0 log 0 = 0: M for a uniformly used codebook, 1 when a single
+        codeword holds everything).  The entropy is summed in fp64."""
+        cs = self.cs
+        n_dead = (cs < threshold).sum(dim=1).to(torch.int32)
+        p = cs.to(torch.float64)
+        p = p / p.sum(dim=1, keepdim=True)
+        perplexity = torch.exp(-torch.xlogy(p, p).sum(dim=1)).to(torch.float32)
+        return n_dead, perplexity
+
     def finish_update(self):
         """Complete an update(defer=True): wait for the EMA-statistics
         all-reduce (multi-GPU; a stream wait, not a host wait) and run the
